@@ -3,12 +3,21 @@
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: one rank per GPU -- under torch.distributed.run when RANK / WORLD_SIZE are
                                                             set, else bench.py starts its own N ranks under it)
+    python bench.py ... --dump-outputs DIR                 (steps in deterministic mode; write what the last timed step computed to DIR/*.npy)
+    python bench.py ... --full                             (also everything else the benchmark measures, see below)
 
 A "step" is one full optimisation step (forward, soft-argmax criterion, backward, gradient all-reduce when N > 1,
 Adam) of the ResNet-50 volumetric-heat-map network on one synthetic 4-view 256x256 batch that is already resident
 in HBM.  Default workload = BASELINE.json configs[1] (fully-supervised SmoothL1 loss, 32 images = 8 groups x 4 views
 per GPU); ``--workload ss`` = configs[2] (pseudo labels from 4-view triangulation inside the step).
-Rank 0 prints ONE JSON line (see the task contract) carrying ``roofline`` and ``cpu_baseline`` objects.
+
+A plain run sets up, runs W warm-up steps and the four untimed steps whose host enqueue cost ``config`` reports, times K
+steps, writes the outputs when ``--dump-outputs`` is given, and rank 0 prints ONE JSON line (see the task contract):
+``value`` images/s, ``ms_per_step`` milliseconds per timed step.  ``--dump-outputs`` runs every step in the library's deterministic
+mode (``config.deterministic``): with the fp32 atomics of the default mode two runs of the same arguments end up far apart, in this
+mode they are bit-identical, at ~1.8x the step time -- the headline figure is a run without it.  ``--full`` adds the rest to the same line: ``roofline``
+(K more steps with HIP events around every launch), the ``workload_ss`` and ``workload_loader`` legs, ``workload_refiner``
+(with ``--refiner-leg``) and ``cpu_baseline``.
 """
 import argparse
 import json
@@ -50,8 +59,13 @@ def parse_args():
                          "gloo with CPU tensors only, it has never run on RCCL (no multi-GPU node has been available)")
     ap.add_argument("--force-grad-sync", action="store_true", help="diagnostic: run the N>1 gradient-bucket path at N=1 (copies "
                     "into the flat buckets, no collective) to price its overhead on one GPU")
-    ap.add_argument("--refiner-leg", action="store_true", help="also time the refiner MLP beside the step (configs[4] names it: post-lift refinement of "
-                    "the batch's poses in inference mode, and one refiner training step at the reference's batch size 64)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline figure: per-kernel roofline, the "
+                    "self-supervised and input-pipeline legs, the CPU baseline (and the refiner leg with --refiner-leg)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="run the steps in the library's deterministic mode (ordered sums "
+                    "instead of fp32 atomics: bit-identical reruns, ~1.8x the step time) and write what the last timed step computed to "
+                    "DIR/<name>.npy (loss, sampled logits, sampled parameters, BatchNorm statistics; float32 / float64, about 32 MB)")
+    ap.add_argument("--refiner-leg", action="store_true", help="with --full: also time the refiner MLP beside the step (configs[4] names it: post-lift "
+                    "refinement of the batch's poses in inference mode, and one refiner training step at the reference's batch size 64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ss-leg", action="store_true", help="skip the extra configs[2] (self-supervised) measurement that rides along")
     ap.add_argument("--no-loader-leg", action="store_true", help="skip the extra measurement with the GPU input pipeline in the step "
@@ -59,7 +73,13 @@ def parse_args():
     ap.add_argument("--cpu-batch", type=int, default=4)
     ap.add_argument("--cpu-baseline-only", action="store_true", help="run ONLY the cpu_baseline leg (no GPU needed) and print it as JSON: in the build "
                     "container this times the reference itself (kind 'reference'), which the GPU box cannot (no /root/reference there)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.refiner_leg and not args.full:
+        ap.error("--refiner-leg is part of --full")
+    if args.dump_outputs and args.graph:
+        ap.error("--dump-outputs runs the steps in deterministic mode, whose per-stream scratch cannot be allocated inside a graph capture: "
+                 "use it without --graph 1")
+    return args
 
 
 def build_problem(args, device, rank, capturable=False):
@@ -429,6 +449,38 @@ def refiner_leg(args, device):
             "train_ms_per_step": round(train_ms, 4), "train_samples_per_s": round(64 / (train_ms * 1e-3), 1), "final_loss": round(float(loss.item()), 6)}
 
 
+DUMP_SAMPLE = 1 << 22          # elements kept of each large output (16 MB as float32)
+
+
+def dump_outputs(path, model, loss, logits):
+    """``--dump-outputs DIR``: what the timed path computed in its LAST step, as DIR/<name>.npy -- the loss the step returns, the
+    logits its forward produced, the parameters and BatchNorm running statistics it left behind.  Logits and parameters are too
+    large to keep whole: a fixed, seeded sample of each (the same positions in every run of the same arguments) sits beside
+    float64 reductions over every element (per-image logit sums, per-tensor parameter norms)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def sample(flat, seed):
+        if flat.numel() <= DUMP_SAMPLE:
+            return flat.float().cpu().numpy()
+        idx = np.sort(np.random.default_rng(seed).integers(0, flat.numel(), DUMP_SAMPLE))
+        return flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+    out = {"loss": loss.detach().float().reshape(1).cpu().numpy()}
+    if logits is not None:
+        lg = logits.detach()
+        out["logits_sample"] = sample(lg.reshape(-1), 1)                  # (logical NCHW order, whatever the memory format)
+        out["logits_sum_per_image"] = lg.sum(dim=tuple(range(1, lg.dim())), dtype=torch.float64).cpu().numpy()
+    params = [p.detach() for _, p in model.named_parameters()]
+    out["param_norms"] = torch.stack([p.double().norm() for p in params]).cpu().numpy()
+    out["params_sample"] = sample(torch.cat([p.reshape(-1).float() for p in params]), 2)
+    stats = [b.detach().reshape(-1).float() for k, b in model.named_buffers() if k.endswith(("running_mean", "running_var"))]
+    if stats:
+        out["bn_running_stats"] = torch.cat(stats).cpu().numpy()
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(out)
+
+
 PMC_FILE = "profiles/r06_pmc_step_families.json"
 
 
@@ -513,6 +565,12 @@ def main():
     device = torch.device("cuda", local)
     hip.load()
     torch.backends.cudnn.benchmark = True        # reference CUDNN.BENCHMARK: true -> MIOpen find mode
+    if args.dump_outputs:
+        # Outputs that two runs can be compared by: every cross-workgroup sum in a fixed order instead of fp32 atomics (the reference's
+        # CUDNN.DETERMINISTIC, the mode the parity tests run in).  With atomics, rounding-level differences in the batch sums grow through
+        # bf16 activations and Adam into losses 20 % apart after 50 steps; in this mode reruns are bit-identical -- at ~1.8x the step time,
+        # so a plain run (the headline figure) keeps the atomics.
+        hip.set_deterministic(True)
 
     use_graph = bool(args.graph)
     cfg, model, criterion, optimizer, images, label, weight, meta, scenes = build_problem(args, device, rank, capturable=use_graph)
@@ -525,6 +583,10 @@ def main():
         grad_sync = epd.BucketedGradSync(model, optimizer=optimizer, collective="direct" if args.allreduce == "direct" else "allreduce")
     n_view = args.views if args.workload == "ss" else None
     # 4-view SS uses the V-view generalisation of the reference's iterative LS solver (V=2 is the reference itself)
+    last_logits = [None]
+    if args.dump_outputs:
+        # the logits of the latest forward (under --graph 1 the captured forward's output, which every replay overwrites)
+        model.register_forward_hook(lambda m, i, o: last_logits.__setitem__(0, o))
 
     def eager_step():
         return train_step(model, criterion, optimizer, images, label, weight, meta=meta, n_view=n_view,
@@ -565,11 +627,23 @@ def main():
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    if world > 1:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=device)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+        elapsed = float(t.item())
+    final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(args.dump_outputs, model, loss, last_logits[0])
+        print("bench.py: wrote %s to %s" % (", ".join(n + ".npy" for n in names), args.dump_outputs), file=sys.stderr, flush=True)
+    deterministic = hip.is_deterministic()
+    if args.dump_outputs:
+        hip.set_deterministic(False)             # (the --full legs below measure the default path)
+    # From here to the JSON line only --full measures anything (the rank inventory below is bookkeeping).
     # Per-kernel durations for the roofline: the SAME step, `steps` more times, now with a HIP event pair around every launch
     # (on the launch stream).  Kept out of the timed region above: ~660 hipEventRecord calls per step cost the host ~8 us each on
     # ROCm 7.2 and turn the step host-bound (10.9 ms instead of 8.9 ms measured), which would falsify `value`.
     glue_times = {}
-    if not use_graph:
+    if args.full and not use_graph:
         hip.timer.reset()
         hip.timer.enabled = True
         hip.glue().timing_collect()              # (clears) -- the C++ glue's launches carry their own HIP events
@@ -584,7 +658,7 @@ def main():
         hip.timer.enabled = False
         hip.glue().timing_enable(False)
         glue_times = hip.glue().timing_collect()
-    if use_graph:
+    if args.full and use_graph:
         # per-kernel durations for the roofline: the same criterion kernels on the same resident logits-sized tensor,
         # launched eagerly with HIP events on the launch stream right after the timed region
         hip.timer.reset()
@@ -596,11 +670,6 @@ def main():
             criterion(probe_logits, label, weight).backward()
         torch.cuda.synchronize()
         hip.timer.enabled = False
-    if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=device)
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        elapsed = float(t.item())
-    final_loss = float(loss.item())
     inventory = rank_inventory(world, device)
     inventory["allreduce"] = args.allreduce
     if grad_sync is not None:
@@ -609,7 +678,7 @@ def main():
     # the other single-GPU workload of BASELINE.json (configs[2]: pseudo labels from multi-view triangulation inside the step)
     # rides along as an extra field of the same JSON line: same model / optimizer state, `steps` more steps, same timing rules
     ss_line = None
-    if args.workload == "fs" and not use_graph and not args.no_ss_leg:
+    if args.full and args.workload == "fs" and not use_graph and not args.no_ss_leg:
         from epipolarpose_amd.hip import DeviceMeta
         ss_meta = DeviceMeta(scenes.meta, device)
 
@@ -661,7 +730,7 @@ def main():
     # the same step fed by the GPU input pipeline: uint8 BGR frames resident in HBM, per batch the reference's augmentation
     # draws + label arithmetic on the host and ONE crop / occlusion / normalisation launch (dataset/synthetic_frames.py); rides along like the SS leg
     loader_line = None
-    if args.workload == "fs" and not use_graph and not args.no_loader_leg and args.batch % args.views == 0:
+    if args.full and args.workload == "fs" and not use_graph and not args.no_loader_leg and args.batch % args.views == 0:
         from epipolarpose_amd.dataset.synthetic_frames import FramePatchLoader, SyntheticFrames
         n_grp = args.batch // args.views
         frames = SyntheticFrames(n_group=2 * n_grp, n_view=args.views, num_joints=args.joints, seed=7 + rank, device=device)
@@ -705,8 +774,6 @@ def main():
         global_batch = args.batch * world
         elem = 4 if args.fp32 else 2
         vox = args.joints * args.depth * (args.image // 4) ** 2
-        ksum = hip.timer.summary()
-        roofline = build_roofline(args, ksum, glue_times, model, images, pair_ms=event_pair_overhead_ms(device))
         line = {
             "metric": "images/sec (4-view 256x256, ResNet-50) at 1/2/4/8 MI355X; MPJPE vs ref",
             "value": round(global_batch * args.steps / elapsed, 2), "unit": "images/s",
@@ -724,17 +791,18 @@ def main():
                        "ranks": inventory,
                        "launch": "hipGraph replay" if use_graph else "eager",
                        "streams": 1 if use_graph or hip.glue().wgrad_stream_mode(-1) == 0 else 2,
+                       "deterministic": deterministic,
                        "host_enqueue_ms_per_step": round(host_elapsed / args.steps * 1e3, 3),
                        "host_enqueue_ms_one_step_empty_queue": round(host_one * 1e3, 3),
                        "host_enqueue_ms_per_step_burst3": round(host_burst * 1e3, 3),
                        "host_blocked_in_hip_ms_per_step": round(max(0.0, host_elapsed / args.steps - host_burst) * 1e3, 3)},
-            "roofline": roofline,
-            "workload_ss": ss_line,
-            "workload_loader": loader_line,
-            "workload_refiner": refiner_line,
         }
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(args, scenes)
+        if args.full:
+            ksum = hip.timer.summary()
+            line["roofline"] = build_roofline(args, ksum, glue_times, model, images, pair_ms=event_pair_overhead_ms(device))
+            line.update(workload_ss=ss_line, workload_loader=loader_line, workload_refiner=refiner_line)
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(args, scenes)
         print(json.dumps(line), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

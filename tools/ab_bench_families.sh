@@ -2,13 +2,16 @@
 # Run on the GPU box (through gpurun): A/B a list of environment settings on bench.py with the per-family figures of the instrumented steps beside the step time.
 # Usage: tools/ab_bench_families.sh <tag> "<ENV=..> <ENV=..>" "-" ...    (one quoted environment per arm; "-" = defaults)
 TAG=$1; shift
-mkdir -p gpurun_out/$TAG
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+cd "$ROOT"
+OUT=${OUT_ROOT:-$ROOT/out}/$TAG
+mkdir -p "$OUT"
 i=0
 for arm in "$@"; do
   i=$((i+1))
   envs=$arm; [ "$arm" = "-" ] && envs=""
-  (env $envs timeout 200 python bench.py --no-cpu-baseline --no-ss-leg --no-loader-leg 2>&1 | tail -1) > gpurun_out/$TAG/arm$i.log
-  python - "$arm" gpurun_out/$TAG/arm$i.log <<'PY'
+  (env $envs timeout 200 python bench.py --full --no-cpu-baseline --no-ss-leg --no-loader-leg 2>&1 | tail -1) > "$OUT/arm$i.log"
+  python - "$arm" "$OUT/arm$i.log" <<'PY'
 import json, sys
 try:
     d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
